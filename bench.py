@@ -14,6 +14,12 @@ Launch (the driver does this for N>1):
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
 Single line of JSON on rank 0 at the end (driver contract).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints that
+line; nothing else is measured.  ``--dump-outputs DIR`` additionally
+writes what the last timed step computed as ``DIR/<name>.npy`` (inputs are
+seeded, so the same arguments give the same inputs in every run).
+``--full`` is where secondary measurements belong; none exist today.
 """
 
 from __future__ import annotations
@@ -72,7 +78,23 @@ def parse_args():
                    help="grpo: enable gradient checkpointing (default OFF: 288 GB "
                    "fits 8B seq-1k activations at micro-batch 16; measured +36%%)")
     p.add_argument("--no-grad-ckpt", action="store_true", help=argparse.SUPPRESS)
-    return p.parse_args()
+    p.add_argument(
+        "--dump-outputs", metavar="DIR", default=None,
+        help="ppo: after the timed steps, write what the last timed step "
+        "computed (per agent: a fixed seeded sample of the rollout rows, "
+        "whole-rollout means, learn stats, policy/critic weights) as "
+        "DIR/<name>.npy so two builds can be compared output for output",
+    )
+    p.add_argument(
+        "--full", action="store_true",
+        help="also run every secondary measurement or check the benchmark "
+        "has; a plain run does only what the headline figure needs (today "
+        "the headline run is all there is, so --full adds nothing)",
+    )
+    args = p.parse_args()
+    if args.dump_outputs and args.workload != "ppo":
+        p.error("--dump-outputs is implemented for --workload ppo only")
+    return args
 
 
 class BenchRunner:
@@ -135,6 +157,10 @@ class BenchRunner:
         for slot in self.pop.local_indices:
             self._init_slot(slot)
         self.step_count = 0
+        # --dump-outputs: set for the last timed step only; bench_step then
+        # keeps each slot's (rollout, learn stats) instead of dropping them
+        self.keep_outputs = False
+        self.last_outputs = {}
 
     def _init_slot(self, slot: int) -> None:
         if torch.cuda.is_available():
@@ -180,7 +206,7 @@ class BenchRunner:
                     collector = GraphedPPOCollector(agent, env, agent.learn_step)
                     self.collectors[slot] = collector
                 flat, stats = collector.collect()
-                agent.learn(flat)
+                learn_stats = agent.learn(flat)
             else:
                 obs, done = self.carried[slot]
                 collect = (
@@ -188,7 +214,10 @@ class BenchRunner:
                 )
                 obs, done, stats = collect(agent, env, buffer, agent.learn_step, obs, done)
                 self.carried[slot] = (obs, done)
-                agent.learn(buffer)
+                learn_stats = agent.learn(buffer)
+                flat = buffer
+            if self.keep_outputs:
+                self.last_outputs[slot] = (flat, learn_stats)
             n = agent.learn_step * self.args.num_envs
             agent.steps[-1] += n
             steps += n
@@ -212,6 +241,61 @@ class BenchRunner:
                 else:
                     self.carried[slot] = (None, None)
         return steps
+
+
+DUMP_ROWS = 4096  # rollout rows written per agent (full rollout: 8.4M rows on GPU)
+
+
+def _as_dump_array(t: torch.Tensor) -> np.ndarray:
+    """float32 stays float32; everything else (int64 actions) goes to
+    float64, which holds those values exactly."""
+    t = t.detach()
+    return t.to(torch.float32 if t.dtype == torch.float32 else torch.float64).cpu().numpy()
+
+
+def dump_outputs(runner: BenchRunner, out_dir: str) -> None:
+    """Write what the last timed step handed back, per local agent slot:
+
+    - ``agent<slot>_<key>.npy``: DUMP_ROWS rows of every rollout tensor
+      (obs, action, reward, done, value, log_prob, advantages, returns);
+      the row sample is fixed (seeded, sorted) so it is the same rows in
+      every run and every build
+    - ``agent<slot>_rollout_mean.npy``: float64 mean of each of those
+      tensors over ALL rows, in sorted key order
+    - ``agent<slot>_learn_stats.npy``: policy_loss, value_loss, entropy,
+      approx_kl returned by ``learn``
+    - ``agent<slot>_params.npy``: actor then critic parameters, flattened,
+      as the population holds them after the step (evolution included
+      when the step ended on an evolution round)
+    - ``agent<slot>_fitness.npy``: the agent's fitness history
+    """
+    os.makedirs(out_dir, exist_ok=True)
+    for slot in sorted(runner.last_outputs):
+        rollout, learn_stats = runner.last_outputs[slot]
+        if not isinstance(rollout, dict):
+            rollout = rollout.get_tensor_batch()
+        rollout = {k: v for k, v in rollout.items() if torch.is_tensor(v)}
+        n = rollout["advantages"].shape[0]
+        rows = np.sort(np.random.default_rng(2024).choice(n, size=min(n, DUMP_ROWS), replace=False))
+        means = []
+        for key in sorted(rollout):
+            t = rollout[key].reshape(n, -1)
+            sel = torch.from_numpy(rows).to(t.device)
+            np.save(os.path.join(out_dir, f"agent{slot}_{key}.npy"),
+                    _as_dump_array(t.index_select(0, sel)))
+            means.append(float(t.double().mean()))
+        np.save(os.path.join(out_dir, f"agent{slot}_rollout_mean.npy"),
+                np.asarray(means, dtype=np.float64))
+        np.save(os.path.join(out_dir, f"agent{slot}_learn_stats.npy"),
+                np.asarray([learn_stats[k] for k in
+                            ("policy_loss", "value_loss", "entropy", "approx_kl")],
+                           dtype=np.float64))
+        agent = runner.pop.agents[slot]
+        params = torch.cat([p.detach().reshape(-1).float()
+                            for net in (agent.actor, agent.critic) for p in net.parameters()])
+        np.save(os.path.join(out_dir, f"agent{slot}_params.npy"), _as_dump_array(params))
+        np.save(os.path.join(out_dir, f"agent{slot}_fitness.npy"),
+                np.asarray(agent.fitness, dtype=np.float64))
 
 
 LLAMA3_8B = dict(
@@ -618,12 +702,16 @@ def main():
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     local_steps = 0
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        runner.keep_outputs = bool(args.dump_outputs) and i == args.steps - 1
         local_steps += runner.bench_step()
     if use_cuda:
         torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        dump_outputs(runner, args.dump_outputs)
 
     # max elapsed over ranks; total env steps over ranks
     if state.is_distributed:

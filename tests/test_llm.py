@@ -1,5 +1,7 @@
 """LLM stack tests: LoRA, fused logprobs, GRPO/SFT/DPO on a tiny random Llama."""
 
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -15,6 +17,10 @@ from agilerl_amd.llm import (
 )
 from agilerl_amd.ops.fused_logprobs import fused_linear_logprobs
 from agilerl_amd.ops.grpo_loss import grpo_policy_loss
+
+# the reference project's training YAMLs, stored verbatim
+REF_CONFIGS = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                           "golden", "reference_configs", "training")
 
 TINY = dict(
     model_type="llama", vocab_size=128, hidden_size=64, intermediate_size=128,
@@ -1094,9 +1100,7 @@ class TestReferenceLlmManifestFields:
         from agilerl_amd.models.manifest import TrainingManifest
         from agilerl_amd.training.trainer import LocalTrainer
 
-        ref = f"/root/reference/configs/training/llm_finetuning/{cfg}"
-        if not os.path.exists(ref):
-            pytest.skip("reference configs absent")
+        ref = os.path.join(REF_CONFIGS, "llm_finetuning", cfg)
         doc = _yaml.safe_load(open(ref))
 
         # local stand-ins for the hub dataset/model (offline image)
@@ -1167,9 +1171,7 @@ class TestReferenceMultiturnManifest:
         from agilerl_amd.models.manifest import TrainingManifest
         from agilerl_amd.training.trainer import LocalTrainer
 
-        ref = f"/root/reference/configs/training/llm_finetuning/{cfg}"
-        if not os.path.exists(ref):
-            pytest.skip("reference configs absent")
+        ref = os.path.join(REF_CONFIGS, "llm_finetuning", cfg)
         doc = _yaml.safe_load(open(ref))
         algo = doc["algorithm"]
         hp = {k: v for k, v in algo.items() if k != "name"}
@@ -1407,9 +1409,7 @@ class TestReferenceDpoManifest:
         from agilerl_amd.models.manifest import TrainingManifest
         from agilerl_amd.training.trainer import LocalTrainer
 
-        ref = "/root/reference/configs/training/llm_finetuning/dpo.yaml"
-        if not os.path.exists(ref):
-            pytest.skip("reference configs absent")
+        ref = os.path.join(REF_CONFIGS, "llm_finetuning", "dpo.yaml")
         doc = _yaml.safe_load(open(ref))
 
         texts = [f"question {i}" for i in range(6)]
@@ -1462,10 +1462,7 @@ class TestReferenceSftManifest:
         from agilerl_amd.models.manifest import TrainingManifest
         from agilerl_amd.training.trainer import LocalTrainer
 
-        ref = "/root/reference/configs/training/llm_finetuning/../sft.yaml"
-        ref = os.path.normpath(ref)
-        if not os.path.exists(ref):
-            pytest.skip("reference configs absent")
+        ref = os.path.join(REF_CONFIGS, "sft.yaml")
         doc = _yaml.safe_load(open(ref))
 
         texts = [f"prompt {i}" for i in range(6)]

@@ -1,5 +1,5 @@
-import warnings, torch, sys
-sys.path.insert(0, "/root/repo")
+import os, warnings, torch, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from agilerl_amd.algorithms.ppo import PPO
 from agilerl_amd.spaces import Box, Discrete
 
